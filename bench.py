@@ -21,7 +21,10 @@ call); one process per GPU, each rank packs and unpacks its own shard of
 independent segments, no data-path collective; scaling is weak.  The
 collectives are the barrier and the max-over-ranks of the timing only.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line
+of the headline figure (`--dump-outputs DIR` also writes what the last timed
+step computed).  With `--full` the run also checks the round trip, times the
+index-free legs and the CPU baseline, and the JSON line also carries
   roofline      the dominant kernel's algorithmic bytes per launch / its mean
                 launch time (HIP events on the launch stream) vs 8 TB/s;
   cpu_baseline  the reference's CPU codec loops (oracle/refloop_oracle.c, a C
@@ -63,17 +66,28 @@ def parse(argv=None):
     ap.add_argument("--chunk-words", type=int, default=128)
     ap.add_argument("--workload", default="config2",
                     choices=["config2", "config3", "carsales", "config4", "config5"])
+    ap.add_argument("--full", action="store_true",
+                    help="also check the round trip and report the per-kernel / roofline "
+                         "figures, the index-free legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (rank 0) "
+                         "as DIR/<name>.npy, float32 / float64, a fixed seeded sample of "
+                         "the larger arrays")
     ap.add_argument("--cpu-sample-words", type=int, default=1 << 25)
     ap.add_argument("--cpu-reps", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--e2e", action="store_true", help="also time host->device->host")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--e2e", action="store_true",
+                    help="with --full: also time host->device->host")
     ap.add_argument("--no-sync", action="store_true",
                     help="pack without the record sync index; unpack walks whole chunks")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reporting only, no GPU (gloo; tests)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -320,6 +334,38 @@ def make_workload(args, ctx, torch, dev, rank):
     return words, offs, n, desc
 
 
+DUMP_SEED = 20240917
+# elements kept per dumped array (55 MB of .npy files at the default size)
+DUMP_CAP = {"packed": 3 << 20, "words": 3 << 18, "sync_index": 1 << 19}
+DUMP_CAP_DEFAULT = 1 << 20
+
+
+def dump_outputs(out_dir, torch, arrays):
+    """--dump-outputs: `arrays` maps a name to a 1-D device tensor (the valid
+    part of an output of the last timed step).  Each is written whole, or as
+    a fixed sample (sorted indices drawn from a generator seeded by the name
+    and the length, so two builds sample the same elements), to
+    DIR/<name>.npy: bytes as float32, 64-bit words as float64 pairs of their
+    32-bit halves, other integers as float64, every value exact."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        cap = DUMP_CAP.get(name, DUMP_CAP_DEFAULT)
+        if t.numel() > cap:
+            rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode()), t.numel()])
+            idx = np.sort(rng.integers(0, t.numel(), size=cap, dtype=np.int64))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.cpu().numpy()
+        if a.dtype == np.uint8:
+            a = a.astype(np.float32)
+        elif name in ("words", "sync_index"):  # bit patterns, not signed numbers
+            a = a.view(np.uint32).astype(np.float64)
+        else:
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -399,7 +445,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        step(args.full)
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -409,10 +455,54 @@ def main():
         from capnp_amd import shard
         elapsed = shard.max_over_ranks(elapsed, device=dev)
 
-    # correctness of the timed work (round trip) — outside the timed region
-    ok = bool(torch.equal(back, words)) and int((status != 0).sum()) == 0
     P = int(poffs[-1].item())
     U = total_words * 8
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from the last step
+        outs = {"packed": packed[:P], "packed_byte_off": poffs, "words": back,
+                "status": status, "consumed": consumed}
+        if sync is not None:
+            outs["sync_index"] = sync
+        dump_outputs(args.dump_outputs, torch, outs)
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * U / GiB / (elapsed / args.steps)
+    line = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "process_group": dist.get_backend() if dist_on else None,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle": {"steps": settle_steps, "ms": round(settle_ms, 1),
+                   "why": "untimed load before the warm-up steps: clocks settle after "
+                          "~30 ms of load (DESIGN.md, Measurement)"},
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": ("synthetic: the reference benchmark's carsales requests (FastRand chain)"
+                 if args.workload == "carsales" else
+                 "synthetic (seeded splitmix64 generator, SURVEY §8d)"),
+        "config": {
+            "workload": desc + ", pack+unpack round trip",
+            "segments_per_gpu": n, "unpacked_bytes_per_gpu": U,
+            "global_unpacked_bytes": world * U, "parallelism": f"shard{world}",
+        },
+        "packed_ratio": round(P / U, 4),
+        "sync_index": sync is not None,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist_on:
+            dist.destroy_process_group()
+        return
+
+    # --full from here.  Correctness of the timed work (round trip), outside
+    # the timed region
+    ok = bool(torch.equal(back, words)) and int((status != 0).sum()) == 0
     pack_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / len(ev)
     unpack_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / len(ev)
     offs_bytes = 8 * (n + 1)
@@ -481,33 +571,8 @@ def main():
     if args.e2e and rank == 0:
         e2e = end_to_end(ctx, torch, words, offs, n, tc, dev)
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * U / GiB / (elapsed / args.steps)
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "process_group": dist.get_backend() if dist_on else None,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle": {"steps": settle_steps, "ms": round(settle_ms, 1),
-                       "why": "untimed load before the warm-up steps: clocks settle after "
-                              "~30 ms of load (DESIGN.md, Measurement)"},
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": ("synthetic: the reference benchmark's carsales requests (FastRand chain)"
-                     if args.workload == "carsales" else
-                     "synthetic (seeded splitmix64 generator, SURVEY §8d)"),
-            "config": {
-                "workload": desc + ", pack+unpack round trip",
-                "segments_per_gpu": n, "unpacked_bytes_per_gpu": U,
-                "global_unpacked_bytes": world * U, "parallelism": f"shard{world}",
-            },
+        line.update({
             "roofline": {
                 "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -526,10 +591,8 @@ def main():
                 round(U / GiB / ((kernels["pack_nosync"]["ms"] +
                                   kernels["unpack_nosync"]["ms"]) * 1e-3), 2)
                 if "unpack_nosync" in kernels else None),
-            "packed_ratio": round(P / U, 4),
-            "sync_index": sync is not None,
             "roundtrip_ok": ok,
-        }
+        })
         if e2e:
             line["e2e"] = e2e
         if not args.no_cpu and world == 1:  # (the CPU baseline is an N=1 figure)

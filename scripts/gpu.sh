@@ -8,8 +8,8 @@
 #   tests              pytest -m gpu over tests/
 #   tests=FILE[,FILE]  pytest -m gpu over the given test files
 #   smoke              __graft_entry__.smoke()
-#   bench              bench.py (the driver's default line)
-#   bench=W            bench.py --workload W
+#   bench              bench.py --full (every figure of the default workload)
+#   bench=W            bench.py --full --workload W
 #   prof=W             rocprofv3 kernel trace + PMC passes of bench.py --workload W (scripts/profile.sh)
 #   trace=W            rocprofv3 --kernel-trace --stats of bench.py --workload W only
 #   py=SCRIPT[,ARG...] python -u scripts/SCRIPT ARG...
@@ -40,16 +40,16 @@ for step in "$@"; do
       w=${arg:-default}
       wa=
       [ -n "$arg" ] && wa="--workload $arg"
-      timeout -k 10 400 python -u bench.py $wa > ${O}_${w}_bench.json 2> ${O}_${w}_bench.err \
+      timeout -k 10 400 python -u bench.py --full $wa > ${O}_${w}_bench.json 2> ${O}_${w}_bench.err \
         || fail "$step" ${O}_${w}_bench.err
       python scripts/bench_summary.py $w ${O}_${w}_bench.json ;;
     prof)
-      timeout -k 10 1000 bash scripts/profile.sh ${O}_prof_${arg} --workload ${arg} --steps 5 --warmup 1 --no-cpu \
+      timeout -k 10 1000 bash scripts/profile.sh ${O}_prof_${arg} --full --workload ${arg} --steps 5 --warmup 1 --no-cpu \
         > ${O}_prof_${arg}.log 2>&1 || fail "$step" ${O}_prof_${arg}.log
       cat ${O}_prof_${arg}/summary.txt ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d ${O}_trace_${arg} -o run --output-format csv \
-        -- python3 bench.py --workload ${arg} --steps 20 --warmup 3 --no-cpu > ${O}_trace_${arg}.json 2> ${O}_trace_${arg}.err \
+        -- python3 bench.py --full --workload ${arg} --steps 20 --warmup 3 --no-cpu > ${O}_trace_${arg}.json 2> ${O}_trace_${arg}.err \
         || fail "$step" ${O}_trace_${arg}.err
       python scripts/bench_summary.py prof ${O}_trace_${arg}.json ;;
     py)

@@ -8,6 +8,6 @@ for round in 1 2; do
   for v in product "$@"; do
     if [ "$v" = product ]; then lib=""; else lib=capnproto-rust_amd/build/abl/libcapnp_packed_$v.so; fi
     echo "{\"variant\": \"$v\", \"round\": $round}" >> "$out"
-    CAPNP_PACKED_LIB=$lib timeout -k 10 300 python3 -u bench.py --workload "$wl" --steps 20 --warmup 3 --no-cpu >> "$out" 2>/dev/null || exit 1
+    CAPNP_PACKED_LIB=$lib timeout -k 10 300 python3 -u bench.py --workload "$wl" --full --steps 20 --warmup 3 --no-cpu >> "$out" 2>/dev/null || exit 1
   done
 done

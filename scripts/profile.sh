@@ -6,7 +6,7 @@ set -euo pipefail
 OUT=${1:-gpurun_out/prof}
 shift || true
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--steps 5 --warmup 1 --no-cpu)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --steps 5 --warmup 1 --no-cpu)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \

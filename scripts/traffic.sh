@@ -5,7 +5,7 @@
 set -uo pipefail
 OUT=$1; shift
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--steps 3 --warmup 1 --no-cpu)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --steps 3 --warmup 1 --no-cpu)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o run --output-format csv -- python3 bench.py "${ARGS[@]}" > "$OUT/fetch.log" 2>&1 || exit 1
