@@ -28,6 +28,10 @@
 extern "C" hipError_t capnp_launch_pack(const uint64_t*, const uint64_t*, uint64_t, uint32_t,
                                         uint8_t*, uint64_t, uint64_t*, uint64_t*, uint32_t*,
                                         hipStream_t);
+extern "C" hipError_t capnp_launch_pack_ex(const uint64_t*, const uint64_t*, uint64_t, uint32_t,
+                                           uint8_t*, uint64_t, uint64_t*, uint64_t*, uint32_t*,
+                                           int, hipStream_t);
+extern "C" int capnp_pack_leaves_state_clean(void);
 extern "C" hipError_t capnp_launch_pack_gap(const uint64_t*, const uint64_t*, uint64_t, uint32_t,
                                             uint8_t*, uint64_t, uint64_t*, uint64_t*,
                                             const uint32_t*, hipStream_t);
@@ -170,6 +174,20 @@ struct capnp_ctx {
     hipStream_t stream = nullptr;
     uint8_t* d_state = nullptr;   // pack look-back records (tiles, groups)
     size_t state_cap = 0;
+    // d_state[0, state_clean) is known to be zero for work ordered after
+    // state_stream's (any stream while state_any): zeroed when allocated, and
+    // left zero by capnp_launch_pack_ex, which uses a prefix of it.  Every
+    // other user of d_state, and a launch that failed, resets the mark, and
+    // the next pack zeroes what it uses itself.
+    // A call captured into a hipGraph is not run when it is enqueued and may
+    // run any number of times later, between any other calls: once a user of
+    // d_state has been captured the mark means nothing, so it is given up for
+    // good (state_untracked) and every pack zeroes the state itself, captured
+    // ones included, as before the mark existed.
+    size_t state_clean = 0;
+    bool state_any = false;
+    bool state_untracked = false;
+    hipStream_t state_stream = nullptr;
     uint8_t* d_stage = nullptr;   // staging for the host APIs (inputs)
     size_t stage_cap = 0;
     uint8_t* d_body = nullptr;    // staging for decoded message bodies
@@ -333,6 +351,20 @@ hipError_t wait_uses(capnp_ctx* ctx) {
     return e;
 }
 
+// Before any use of d_state on stream s: a capturing stream ends the
+// tracking of the clean state (capnp_ctx::state_untracked).
+void note_state_use(capnp_ctx* ctx, hipStream_t s) {
+    if (ctx->state_untracked) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        ctx->state_untracked = true;
+        ctx->state_clean = 0;
+    }
+}
+
+// (A growth frees, allocates and zeroes the workspace with the device
+// synchronised: one more reason why capnp_ctx_reserve has to come before any
+// capture and keeps this out of the steady state.)
 capnp_status ensure_state(capnp_ctx* ctx, size_t bytes) {
     if (bytes <= ctx->state_cap) return CAPNP_OK;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -353,6 +385,11 @@ capnp_status ensure_state(capnp_ctx* ctx, size_t bytes) {
     HIP_TRY(hipMalloc(&ctx->d_state, cap));
 #endif
     ctx->state_cap = cap;
+    ctx->state_clean = 0;
+    HIP_TRY(hipMemset(ctx->d_state, 0, cap));
+    HIP_TRY(hipStreamSynchronize(nullptr));  // (the fill is done before any stream's next work)
+    ctx->state_clean = ctx->state_untracked ? 0 : cap;
+    ctx->state_any = true;
     return CAPNP_OK;
 }
 
@@ -769,6 +806,8 @@ capnp_status pack_batch_dev(capnp_ctx* ctx, const uint64_t* d_words, const uint6
             if (st != CAPNP_OK) return st;
             st = ensure_buf(ctx, &ctx->d_pwt, &ctx->pwt_cap, capnp_pack_wt_ws_bytes(wr[0], wr[1]));
             if (st != CAPNP_OK) return st;
+            note_state_use(ctx, s);
+            ctx->state_clean = 0;  // (the word tiles zero the state themselves and leave it used)
             HIP_TRY(capnp_launch_pack_wt(d_words, d_off, n, d_out, cap, d_out_off,
                                          reinterpret_cast<uint64_t*>(ctx->d_state), ctx->d_pwt,
                                          ctx->pwt_cap, d_sync, wr[0], wr[1], s));
@@ -781,8 +820,24 @@ capnp_status pack_batch_dev(capnp_ctx* ctx, const uint64_t* d_words, const uint6
     const size_t sb = state_bytes_for(n, tc);
     capnp_status st = ensure_state(ctx, sb);
     if (st != CAPNP_OK) return st;
-    HIP_TRY(capnp_launch_pack(d_words, d_off, n, tc, d_out, cap, d_out_off,
-                              reinterpret_cast<uint64_t*>(ctx->d_state), d_sync, s));
+    note_state_use(ctx, s);
+    const size_t used = capnp_pack_state_bytes(n, tc);
+    const size_t was_clean = ctx->state_clean;
+    const bool clean = used <= was_clean && (ctx->state_any || ctx->state_stream == s);
+    ctx->state_clean = 0;  // (until the launch has succeeded)
+    HIP_TRY(capnp_launch_pack_ex(d_words, d_off, n, tc, d_out, cap, d_out_off,
+                                 reinterpret_cast<uint64_t*>(ctx->d_state), d_sync, clean ? 1 : 0,
+                                 s));
+    if (n == 0) {
+        ctx->state_clean = was_clean;  // (an empty batch leaves the state alone)
+    } else {
+        // (zeroed by the call when not clean before, and left zero after use)
+        ctx->state_clean = capnp_pack_leaves_state_clean() && !ctx->state_untracked
+                               ? (clean ? was_clean : used)
+                               : 0;
+        ctx->state_any = false;
+        ctx->state_stream = s;
+    }
     return CAPNP_OK;
 }
 
@@ -1575,6 +1630,8 @@ capnp_status capnp_gpu_write_messages(capnp_ctx* ctx, const uint64_t* d_words,
             const uint32_t tc = tile_chunks_for(total_words, total_segs);
             st = ensure_state(ctx, state_bytes_for(total_segs, tc));
             if (st != CAPNP_OK) return st;
+            note_state_use(ctx, s);
+            ctx->state_clean = 0;  // (the gap pack zeroes the state itself and leaves it used)
             HIP_TRY(capnp_launch_pack_gap(d_words, d_seg_word_off, total_segs, tc, d_out, out_cap,
                                           cboff, reinterpret_cast<uint64_t*>(ctx->d_state), gap,
                                           s));

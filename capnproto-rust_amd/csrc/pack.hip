@@ -678,55 +678,31 @@ __device__ __forceinline__ void copy_out(const uint8_t* region, uint8_t* __restr
 }
 
 // The same for a whole tile whose waves' bytes lie back to back in LDS
-// (PACK_TILECOPY): the tile's 16-byte output blocks are cut into one range
-// per wave, and only the tile's two edges take byte stores.
+// (PACK_TILECOPY), any `out` alignment.  The tile's bytes are cut into
+// 16-byte blocks in LDS coordinates, one range per wave: block k =
+// region[16 k, 16 k + 16) is one aligned LDS read, stored to out + D0 + 16 k
+// at whatever alignment D0 has (global stores take any byte address); only
+// the partial block at the tile's end takes byte stores.  (Blocks cut in
+// output coordinates, as copy_out's, took two LDS reads and a funnel shift
+// under a 4-way branch per block: 5 us slower at config 2, DESIGN.md.)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 __attribute__((aligned(1))) u32x4_unaligned;
+
 __device__ __forceinline__ void copy_out_tile(const uint8_t* region, uint8_t* __restrict__ out,
                                               uint64_t D0, uint64_t len, uint64_t cap,
                                               uint32_t lane, uint32_t wave) {
     const uint64_t lo = D0;
     const uint64_t hi = (D0 + len < cap) ? D0 + len : cap;
     if (hi <= lo) return;
-    const uint64_t a = (lo + 15) & ~15ull, b = hi & ~15ull;
-    if (a > b) {
-        if (wave == 0 && lane < hi - lo) out[lo + lane] = region[lane];
-        return;
-    }
-    if (wave == 0 && lane < a - lo) out[lo + lane] = region[lane];
-    if (wave == kWaves - 1 && lane < hi - b) out[b + lane] = region[(b - D0) + lane];
-    const uint32_t nb = (uint32_t)((b - a) >> 4);
+    const uint32_t L = (uint32_t)(hi - lo);  // (<= len: a tile's bytes)
+    const uint32_t nb = L >> 4;
     const uint32_t k0 = nb * wave / kWaves, k1 = nb * (wave + 1) / kWaves;
-    const uint32_t m = (uint32_t)((a - D0) & 15);  // source misalignment (uniform)
-    const uint32_t q = m >> 2, sb = m & 3;
+    uint8_t* const dst = out + lo;
     for (uint32_t k = k0 + lane; k < k1; k += CAPNP_WAVE) {
-        const uint64_t blk = a + 16ull * k;
-        const uint32_t s = (uint32_t)(blk - D0) & ~15u;
-        const uint4 A = *reinterpret_cast<const uint4*>(region + s);
-        const uint4 B = *reinterpret_cast<const uint4*>(region + s + 16);
-        const uint32_t w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
-        uint4 o;
-        if (q == 0) {
-            o = make_uint4(__builtin_amdgcn_alignbyte(w[1], w[0], sb),
-                           __builtin_amdgcn_alignbyte(w[2], w[1], sb),
-                           __builtin_amdgcn_alignbyte(w[3], w[2], sb),
-                           __builtin_amdgcn_alignbyte(w[4], w[3], sb));
-        } else if (q == 1) {
-            o = make_uint4(__builtin_amdgcn_alignbyte(w[2], w[1], sb),
-                           __builtin_amdgcn_alignbyte(w[3], w[2], sb),
-                           __builtin_amdgcn_alignbyte(w[4], w[3], sb),
-                           __builtin_amdgcn_alignbyte(w[5], w[4], sb));
-        } else if (q == 2) {
-            o = make_uint4(__builtin_amdgcn_alignbyte(w[3], w[2], sb),
-                           __builtin_amdgcn_alignbyte(w[4], w[3], sb),
-                           __builtin_amdgcn_alignbyte(w[5], w[4], sb),
-                           __builtin_amdgcn_alignbyte(w[6], w[5], sb));
-        } else {
-            o = make_uint4(__builtin_amdgcn_alignbyte(w[4], w[3], sb),
-                           __builtin_amdgcn_alignbyte(w[5], w[4], sb),
-                           __builtin_amdgcn_alignbyte(w[6], w[5], sb),
-                           __builtin_amdgcn_alignbyte(w[7], w[6], sb));
-        }
-        *reinterpret_cast<uint4*>(out + blk) = o;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(region + 16u * k);
+        *reinterpret_cast<u32x4_unaligned*>(dst + 16u * k) = v;
     }
+    if (wave == kWaves - 1 && lane < L - 16u * nb) dst[16u * nb + lane] = region[16u * nb + lane];
 }
 
 // Streaming path: wave w owns chunks w, w+4, ...  MODE_SIZE fills
@@ -2383,9 +2359,8 @@ pack_cs_kernel(const uint64_t* __restrict__ in, const uint64_t* __restrict__ chu
     for (uint32_t i = tid; i < nc; i += kThreads) out_off[c0 + i] = sm.chunk_pos[i];
     if (fits) {
         if (PACK_TILECOPY && !(PACK_ABL & 8)) {
-            const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
-            const uint64_t D0 = lds_u64(&sm.chunk_pos[0]) + mis;
-            copy_out_tile(&sm.stage[0][0], out - mis, D0, tbytes, out_cap + mis, lane, wave);
+            copy_out_tile(&sm.stage[0][0], out, lds_u64(&sm.chunk_pos[0]), tbytes, out_cap, lane,
+                          wave);
         } else if (nw && !(PACK_ABL & 8)) {
             const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
             const uint64_t D0 = lds_u64(&sm.chunk_pos[wc0]) + mis;
@@ -2405,12 +2380,20 @@ pack_cs_kernel(const uint64_t* __restrict__ in, const uint64_t* __restrict__ chu
 // Tiles whose staged ranges overflowed (ovf[t] set by pack_kernel, after its
 // look-back wrote the chunks' offsets): the streaming path writes their
 // bytes at those offsets.  One lane per tile finds them; a few workgroups.
+// It is the call's last kernel, so with nrec != 0 (PACK_SELFCLEAN) it also
+// leaves the workspace as the next call needs it: every workgroup clears the
+// flags it read (no other workgroup reads them), and the rec[0, nrec)
+// look-back records, which nothing reads by now, are cleared by grid stride.
+#ifndef PACK_SELFCLEAN
+#define PACK_SELFCLEAN 1  // pack_ovf_kernel<false> zeroes the state for the next call
+#endif
 template <bool GAP>
 __global__ void __launch_bounds__(kThreads)
 pack_ovf_kernel(const uint64_t* __restrict__ in, const uint64_t* __restrict__ chunk_off,
                 uint64_t nchunks, uint32_t tc, uint8_t* __restrict__ out, uint64_t out_cap,
-                const uint64_t* __restrict__ out_off, const uint8_t* __restrict__ ovf,
-                uint64_t ntiles, const uint32_t* __restrict__ gap) {
+                const uint64_t* __restrict__ out_off, uint8_t* __restrict__ ovf,
+                uint64_t ntiles, const uint32_t* __restrict__ gap,
+                uint64_t* __restrict__ rec = nullptr, uint64_t nrec = 0) {
     __shared__ Smem<GAP> sm;
     __shared__ uint32_t lst[kThreads];
     __shared__ uint32_t nl;
@@ -2425,7 +2408,10 @@ pack_ovf_kernel(const uint64_t* __restrict__ in, const uint64_t* __restrict__ ch
          base += (uint64_t)gridDim.x * kThreads) {
         if (tid == 0) nl = 0;
         __syncthreads();
-        if (base + tid < ntiles && ovf[base + tid]) lst[atomicAdd(&nl, 1u)] = tid;
+        if (base + tid < ntiles && ovf[base + tid]) {
+            lst[atomicAdd(&nl, 1u)] = tid;
+            if (nrec) ovf[base + tid] = 0;
+        }
         __syncthreads();
         const uint32_t n = nl;
         for (uint32_t k = 0; k < n; k++) {
@@ -2445,6 +2431,9 @@ pack_ovf_kernel(const uint64_t* __restrict__ in, const uint64_t* __restrict__ ch
         }
         __syncthreads();
     }
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + tid; i < nrec;
+         i += (uint64_t)gridDim.x * kThreads)
+        rec[i] = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -3300,7 +3289,9 @@ msg_pack_service(const uint64_t* line, uint64_t* mark, uint32_t gen, uint64_t id
 // 64-word steps); the host picks chunks_per_tile ~ this / mean chunk words.
 extern "C" uint32_t capnp_pack_tile_words(void) { return kWaves * 64 * kStageSteps; }
 
-// Workspace layout (zeroed every call; uncached memory, capi.hip):
+// Workspace layout (zero at every call's start: zeroed by the call, or known
+// to be left zero by the previous one, capnp_launch_pack_ex; uncached memory,
+// capi.hip):
 // ts[ntiles] tile records, then gs[ngroups] group records.
 // Look-back records above the tiles': level 1 (groups of 64 tiles), then the
 // deeper levels of lookback_ml (blocks of 64^k tiles) up to one record.
@@ -3327,19 +3318,30 @@ static dim3 pack_ovf_grid(uint64_t ntiles) {
     return dim3((uint32_t)(g < 1024 ? g : 1024));
 }
 
-extern "C" hipError_t capnp_launch_pack(const uint64_t* d_in, const uint64_t* d_chunk_off,
-                                        uint64_t nchunks, uint32_t tc, uint8_t* d_out,
-                                        uint64_t out_cap, uint64_t* d_out_off,
-                                        uint64_t* d_state, uint32_t* d_sync,
-                                        hipStream_t stream) {
+// Whether a completed capnp_launch_pack_ex leaves the first
+// capnp_pack_state_bytes(nchunks, tc) bytes of d_state zero (PACK_SELFCLEAN).
+extern "C" int capnp_pack_leaves_state_clean(void) { return PACK_SELFCLEAN ? 1 : 0; }
+
+// state_clean != 0: the caller knows that d_state is all zero up to this
+// call's capnp_pack_state_bytes (freshly zeroed, or left so by the previous
+// capnp_launch_pack_ex on this stream, see capnp_pack_leaves_state_clean), so
+// it is not zeroed here.
+extern "C" hipError_t capnp_launch_pack_ex(const uint64_t* d_in, const uint64_t* d_chunk_off,
+                                           uint64_t nchunks, uint32_t tc, uint8_t* d_out,
+                                           uint64_t out_cap, uint64_t* d_out_off,
+                                           uint64_t* d_state, uint32_t* d_sync,
+                                           int state_clean, hipStream_t stream) {
     if (tc == 0 || tc > kMaxTileChunks) return hipErrorInvalidValue;
     const uint64_t ntiles = (nchunks + tc - 1) / tc;
     if (nchunks == 0) {
         return hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream);
     }
-    hipError_t e = hipMemsetAsync(d_state, 0, capnp_pack_state_bytes(nchunks, tc), stream);
-    if (e != hipSuccess) return e;
+    if (!state_clean) {
+        hipError_t e = hipMemsetAsync(d_state, 0, capnp_pack_state_bytes(nchunks, tc), stream);
+        if (e != hipSuccess) return e;
+    }
     uint8_t* ovf = pack_ovf_flags(d_state, ntiles);
+    const uint64_t nrec = PACK_SELFCLEAN ? ntiles + level_record_count(ntiles) : 0;
     if (tc == kWaves * kCsSteps) {
         // chunks of at most 128 words (tc chosen for a mean of 65-128 words;
         // a tile with a longer chunk takes the streaming size pass)
@@ -3362,8 +3364,18 @@ extern "C" hipError_t capnp_launch_pack(const uint64_t* d_in, const uint64_t* d_
     }
     hipLaunchKernelGGL((pack_ovf_kernel<false>), pack_ovf_grid(ntiles), dim3(kThreads), 0, stream,
                        d_in, d_chunk_off, nchunks, tc, d_out, out_cap, d_out_off, ovf, ntiles,
-                       nullptr);
+                       nullptr, d_state, nrec);
     return hipGetLastError();
+}
+
+// The stateless form: the state is zeroed on every call.
+extern "C" hipError_t capnp_launch_pack(const uint64_t* d_in, const uint64_t* d_chunk_off,
+                                        uint64_t nchunks, uint32_t tc, uint8_t* d_out,
+                                        uint64_t out_cap, uint64_t* d_out_off,
+                                        uint64_t* d_state, uint32_t* d_sync,
+                                        hipStream_t stream) {
+    return capnp_launch_pack_ex(d_in, d_chunk_off, nchunks, tc, d_out, out_cap, d_out_off,
+                                d_state, d_sync, 0, stream);
 }
 
 // Pack with a leading gap of d_gap[c] bytes before every chunk c: out_off[c]
