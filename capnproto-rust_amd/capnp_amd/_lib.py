@@ -50,7 +50,7 @@ EXPORTS = [
     "capnp_packed_reader_read_message", "capnp_packed_reader_buffered",
     "capnp_gpu_find_messages",
     "capnp_gpu_read_message_stream", "capnp_abi_version", "capnp_resync_max_passes",
-    "capnp_unpack_prefix",
+    "capnp_unpack_prefix", "capnp_gpu_unpack_batch_select",
 ]
 ABI_VERSION = 6  # include/capnp_packed.h CAPNP_ABI_VERSION
 
@@ -120,6 +120,8 @@ def lib():
     L.capnp_gpu_unpack_batch_sync.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.capnp_gpu_pack_batch_sync_tuned.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, u32, vp]
     L.capnp_gpu_unpack_batch_sync_tuned.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp]
+    L.capnp_gpu_unpack_batch_select.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp,
+                                                vp, vp]
     L.capnp_ctx_reserve.argtypes = [vp, sz]
     L.capnp_gpu_unpack_batch_resync.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     L.capnp_resync_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -179,6 +179,45 @@ class Context:
                                chunks_per_tile)
         return words[:total], status[:n], consumed[:n]
 
+    def unpack_select_into(self, packed, in_byte_off, chunk_word_off, ids, words, out_word_off,
+                           status, consumed=None, sync=None, stream=None):
+        """Enqueue the decode of chunks `ids` (int64, any order, repeats
+        allowed) of a packed store (capnp_gpu_unpack_batch_select): the
+        store's `in_byte_off` / `chunk_word_off` (int64, nstore + 1) as
+        pack_batch_into left them.  Entry i's words land at
+        words[out_word_off[i]:out_word_off[i + 1]]; `out_word_off` (int64,
+        len(ids) + 1) is written by the call, `status` (int32) and `consumed`
+        (int64, optional) have len(ids) entries.  `sync` = the store's record
+        sync index, optional.  No host synchronisation."""
+        nstore = in_byte_off.numel() - 1
+        st = _lib.lib().capnp_gpu_unpack_batch_select(
+            self._h, _ptr(packed), _ptr(in_byte_off), _ptr(chunk_word_off), nstore, _ptr(ids),
+            ids.numel(), _ptr(sync), _ptr(words), words.numel(), _ptr(out_word_off),
+            _ptr(status), _ptr(consumed), self._stream(stream))
+        _check(st, self._h)
+
+    def unpack_select(self, packed, in_byte_off, chunk_word_off, ids, sync=None):
+        """Decode chunks `ids` of a packed store -> (words, out_word_off,
+        status, consumed).  Synchronises the stream once to read the total
+        size (ids outside the store, which decode to nothing, count as 0)."""
+        import torch
+        dev = in_byte_off.device
+        nstore = in_byte_off.numel() - 1
+        nsel = ids.numel()
+        total = 0
+        if nsel and nstore > 0:
+            ok = (ids >= 0) & (ids < nstore)
+            idc = torch.where(ok, ids, torch.zeros_like(ids))
+            ln = (chunk_word_off[idc + 1] - chunk_word_off[idc]).clamp(min=0)
+            total = int(torch.where(ok, ln, torch.zeros_like(ln)).sum().item())
+        words = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+        out_word_off = torch.empty(nsel + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(max(nsel, 1), dtype=torch.int32, device=dev)
+        consumed = torch.empty(max(nsel, 1), dtype=torch.int64, device=dev)
+        self.unpack_select_into(packed, in_byte_off, chunk_word_off, ids, words, out_word_off,
+                                status, consumed, sync=sync)
+        return words[:total], out_word_off, status[:nsel], consumed[:nsel]
+
     def write_messages(self, words, seg_word_off, msg_seg_off, out=None, stream=None):
         """serialize_packed::write_message for a batch of messages on the
         device (capnp_gpu_write_messages): int64 device tensors `words`

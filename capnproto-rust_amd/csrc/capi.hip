@@ -89,6 +89,12 @@ extern "C" hipError_t capnp_scan_counts(const uint64_t*, uint64_t, uint64_t*, vo
                                         hipStream_t);
 extern "C" size_t capnp_scan_counts_tmp_bytes(uint64_t n);
 extern "C" size_t capnp_unpack_wt_ws_bytes(uint64_t wlo, uint64_t whi);
+extern "C" size_t capnp_unpack_select_ws_bytes(uint64_t nsel);
+extern "C" hipError_t capnp_launch_unpack_select(const uint8_t*, const uint64_t*, const uint64_t*,
+                                                 uint64_t, const uint64_t*, uint64_t,
+                                                 const uint32_t*, uint64_t*, uint64_t, uint64_t*,
+                                                 int32_t*, uint64_t*, uint8_t*, size_t,
+                                                 hipStream_t);
 extern "C" uint64_t capnp_pack_wt_tiles(uint64_t wlo, uint64_t whi);
 extern "C" size_t capnp_pack_wt_ws_bytes(uint64_t wlo, uint64_t whi);
 extern "C" hipError_t capnp_launch_pack_wt(const uint64_t*, const uint64_t*, uint64_t, uint8_t*,
@@ -208,6 +214,8 @@ struct capnp_ctx {
     size_t resync_cap = 0;
     uint8_t* d_wt = nullptr;  // word-tile unpack: per-tile plans and piece flags
     size_t wt_cap = 0;
+    uint8_t* d_sel = nullptr;  // selective unpack: entry records, word counts, overflow list
+    size_t sel_cap = 0;
     uint8_t* d_pwt = nullptr;  // word-tile pack: range map and tile offsets
     size_t pwt_cap = 0;
     uint8_t* d_stream_words = nullptr;  // message discovery: the stream decoded to words
@@ -1051,6 +1059,7 @@ void capnp_ctx_destroy(capnp_ctx* ctx) {
     if (ctx->d_msg) (void)hipFree(ctx->d_msg);
     if (ctx->d_resync) (void)hipFree(ctx->d_resync);
     if (ctx->d_wt) (void)hipFree(ctx->d_wt);
+    if (ctx->d_sel) (void)hipFree(ctx->d_sel);
     if (ctx->d_pwt) (void)hipFree(ctx->d_pwt);
     if (ctx->ev_resync) (void)hipEventDestroy(ctx->ev_resync);
     for (int k = 0; k < capnp_ctx::kUseSlots; k++)
@@ -1078,7 +1087,11 @@ const char* capnp_ctx_last_error(capnp_ctx* ctx) { return ctx ? ctx->err.c_str()
 
 capnp_status capnp_ctx_reserve(capnp_ctx* ctx, size_t max_chunks) {
     if (!ctx) return CAPNP_E_INVALID_ARGUMENT;
-    return ensure_state(ctx, state_bytes_for(max_chunks, 1));
+    const capnp_status st = ensure_state(ctx, state_bytes_for(max_chunks, 1));
+    if (st != CAPNP_OK) return st;
+    // (capnp_gpu_unpack_batch_select of up to max_chunks entries)
+    if (max_chunks >= (size_t)INT32_MAX) return CAPNP_OK;
+    return ensure_buf(ctx, &ctx->d_sel, &ctx->sel_cap, capnp_unpack_select_ws_bytes(max_chunks));
 }
 
 capnp_status capnp_gpu_pack_batch(capnp_ctx* ctx, const uint64_t* d_words,
@@ -1187,6 +1200,32 @@ capnp_status capnp_gpu_unpack_batch_tuned(capnp_ctx* ctx, const uint8_t* d_packe
                                           uint32_t chunks_per_tile, void* stream) {
     return unpack_batch_dev(ctx, d_packed, d_in_byte_off, nchunks, d_words, d_out_word_off,
                             d_status, d_consumed, chunks_per_tile, stream);
+}
+
+capnp_status capnp_gpu_unpack_batch_select(capnp_ctx* ctx, const uint8_t* d_packed,
+                                           const uint64_t* d_in_byte_off,
+                                           const uint64_t* d_chunk_word_off, size_t nstore,
+                                           const uint64_t* d_ids, size_t nsel,
+                                           const uint32_t* d_sync, uint64_t* d_words,
+                                           size_t words_cap, uint64_t* d_out_word_off,
+                                           int32_t* d_status, uint64_t* d_consumed,
+                                           void* stream) {
+    if (!ctx || !d_out_word_off) return CAPNP_E_INVALID_ARGUMENT;
+    if (nsel && (!d_ids || !d_status || (nstore && (!d_in_byte_off || !d_chunk_word_off))))
+        return CAPNP_E_INVALID_ARGUMENT;
+    // (the scan's count is an int, and it covers nsel entries)
+    if (nsel >= (size_t)INT32_MAX) return CAPNP_E_INVALID_ARGUMENT;
+    hipStream_t s = pick(ctx, stream);
+    UseMark um{ctx, s};
+    if (nsel) {
+        const capnp_status st =
+            ensure_buf(ctx, &ctx->d_sel, &ctx->sel_cap, capnp_unpack_select_ws_bytes(nsel));
+        if (st != CAPNP_OK) return st;
+    }
+    HIP_TRY(capnp_launch_unpack_select(d_packed, d_in_byte_off, d_chunk_word_off, nstore, d_ids,
+                                       nsel, d_sync, d_words, words_cap, d_out_word_off, d_status,
+                                       d_consumed, ctx->d_sel, ctx->sel_cap, s));
+    return CAPNP_OK;
 }
 
 size_t capnp_sync_index_entries(size_t total_words) {

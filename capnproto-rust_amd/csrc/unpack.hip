@@ -565,6 +565,7 @@ struct StageSmemT {
     static constexpr uint32_t kTW = TW, kTB = TB;
     static constexpr uint32_t kDummy = TW;  // dpos[kDummy + 2 lane]: dummy slots
     static constexpr uint32_t kSeg = ENT ? TW / kSyncWords + 2 : 1;
+    static constexpr bool kGather = false;  // chunk c ends where chunk c + 1 starts
     union {
         uint64_t sel[SEL ? 256 : 1];  // expand_selector(tag): 0x00 -> zeros, 0xFF -> identity
     };
@@ -585,6 +586,17 @@ struct StageSmemT {
     alignas(16) uint16_t dpos[TW + 2 * CAPNP_WAVE];  // [TW + 2 lane]: dummy slots
 };
 using StageSmem = StageSmemT<kTileWords, kTileBytes>;
+
+// LDS position of the end of chunk c's packed bytes.  The batch tiles stage
+// one contiguous range (cp[c + 1]); the select tiles gather their chunks, each
+// at its own 16-byte misalignment, and keep the ends in a table of their own.
+template <class SM>
+__device__ __forceinline__ uint32_t chunk_pe(const SM& S, uint32_t c) {
+    if constexpr (SM::kGather)
+        return S.ce[c];
+    else
+        return S.cp[c + 1];
+}
 // The overflow kernels' staged sub-tiles without the index: their LDS holds
 // the long-unit tables anyway, room for 4x the words of a tile, so a tile
 // that overflows the fit kernel's tables by its words (zero-run units: the
@@ -1156,7 +1168,7 @@ __device__ __forceinline__ void spec_seg_tile(SM& S, uint64_t ca, uint32_t nc,
     uint32_t cs = 0, pe = 0, n = 0, sb = 0, se = 0;
     if (act) {
         cs = S.cp[c];
-        pe = S.cp[c + 1];
+        pe = chunk_pe(S, c);
         n = S.cw[c + 1] - S.cw[c];
         const uint32_t len = pe - cs;
         sb = cs + (uint32_t)(((uint64_t)len * j) >> lg);
@@ -1349,12 +1361,12 @@ __device__ __forceinline__ void spec_seg_tile(SM& S, uint64_t ca, uint32_t nc,
             for (uint32_t i = wa; i < wz; i++) S.dpos[i] = kNone;
             int32_t st;
             uint32_t used;
-            walk_chunk(S, S.cp[tid], S.cp[tid + 1], wa, wz - wa, st, used);
+            walk_chunk(S, S.cp[tid], chunk_pe(S, tid), wa, wz - wa, st, used);
             status[cc] = st;
             if (consumed) consumed[cc] = used;
         } else {
             status[cc] = ST_OK;
-            if (consumed) consumed[cc] = nn ? S.cp[tid + 1] - S.cp[tid] : 0u;
+            if (consumed) consumed[cc] = nn ? chunk_pe(S, tid) - S.cp[tid] : 0u;
         }
     }
 }
@@ -3185,6 +3197,418 @@ msg_read_service(const uint64_t* line, uint64_t* mark, uint32_t gen, uint64_t id
     svc_exit(mark, gen, tid);
 }
 
+// ---------------------------------------------------------------------------
+// Selective unpack (capnp_gpu_unpack_batch_select): entry i decodes chunk
+// ids[i] of a packed store to the words [out_off[i], out_off[i + 1]) of a
+// compact output.
+//   prep    one thread per entry validates its id and the store's offsets of
+//           that chunk alone and writes a record {packed start, first store
+//           word, packed length, flags} and the entry's word count; an
+//           exclusive sum of the counts (hipcub, the caller) gives out_off.
+//   tile    one workgroup per kSelTile consecutive entries.  Their packed
+//           bytes are scattered over the store, so the staging gathers them:
+//           chunk c lands at LDS byte 16 (its first block) + (address & 15),
+//           in 16-byte blocks of its own (aligned 16-byte loads, nothing read
+//           outside the blocks that overlap the chunk), and the chunk ends
+//           are a table of their own (SelSmem::ce, chunk_pe).  The output
+//           words of a tile are one contiguous range, so the expansion is the
+//           batch decode's.
+//   walk    without the index: the batch decode's segment walk
+//           (spec_seg_tile).  With it: the index is addressed by the store's
+//           word space, so each chunk is cut where ITS store words cross a
+//           multiple of kSyncWords (sel_walk_seg), one thread per segment;
+//           the walks must meet inside the chunk and end at its packed end,
+//           anything else sends the chunk to the exact walk.
+//   overflow  a tile that does not fit the tables at once is put on a list;
+//           select_ovf_kernel cuts it into sub-tiles that fit (index-free)
+//           and gives a chunk too large alone to the long-unit decode
+//           (unpack_long), whose offset arrays are indexed by one chunk
+//           number: it gets the store's byte offsets shifted by id - i.
+// An entry whose words end past words_cap is not decoded (those entries are a
+// suffix of the selection: the offsets are a running sum).
+constexpr uint32_t kSelTile = kSegChunks;          // entries per workgroup: the segment walk's tiles
+constexpr uint32_t kSelBlocks = kTileBytes / 16;   // staged 16-byte blocks per sub-tile
+// sync segments of a sub-tile: a chunk of n words has at most n / 8 + 2
+constexpr uint32_t kSelSegs = kTileWords / kSyncWords + 2 * kSelTile;
+constexpr uint32_t kSelInvalid = 1;  // id or the store's offsets of the chunk refused
+constexpr uint32_t kSelHuge = 2;     // packed length past 31 bits (long-unit decode)
+constexpr uint32_t kSelShort = 4;    // the entry's words end past words_cap
+constexpr uint32_t kSelOvfGrid = 1024;
+
+struct SelRec {
+    uint64_t pb;     // the chunk's first packed byte
+    uint64_t w0;     // its first word in the store's word space (the index's)
+    uint32_t len;    // its packed length (kSelHuge: clamped)
+    uint32_t flags;
+    uint64_t pad;
+};
+static_assert(sizeof(SelRec) == 32, "two 16-byte loads per entry");
+
+struct SelSmem : StageSmemT<kTileWords, kTileBytes, true, false> {
+    static constexpr bool kGather = true;
+    uint32_t ce[kSelTile];  // chunk packed ends (LDS positions)
+    uint8_t fl[kSelTile];   // entry flags
+    uint8_t rr[kSelTile];   // the chunk's first store word modulo kSyncWords
+};
+union SelUSmem {
+    USmem u;  // (the long-unit decode's view)
+    SelSmem st;
+};
+
+__global__ void __launch_bounds__(256)
+select_prep_kernel(const uint64_t* __restrict__ in_off, const uint64_t* __restrict__ word_off,
+                   uint64_t nstore, const uint64_t* __restrict__ ids, uint64_t nsel,
+                   SelRec* __restrict__ rec, uint64_t* __restrict__ len,
+                   uint32_t* __restrict__ novf) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *novf = 0;
+    if (i >= nsel) return;
+    const uint64_t id = ids[i];
+    SelRec r{0, 0, 0, kSelInvalid, 0};
+    uint64_t n = 0;
+    if (id < nstore) {
+        const uint64_t b0 = in_off[id], b1 = in_off[id + 1];
+        const uint64_t w0 = word_off[id], w1 = word_off[id + 1];
+        if (b0 <= b1 && w0 <= w1) {
+            const uint64_t L = b1 - b0;
+            r.pb = b0;
+            r.w0 = w0;
+            r.len = L > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)L;
+            r.flags = L > 0x7FFFFFFFull ? kSelHuge : 0u;
+            n = w1 - w0;
+        }
+    }
+    rec[i] = r;
+    len[i] = n;
+}
+
+// Lane j < nc of every wave: entry ia + j of the tile.
+struct SelLane {
+    uint64_t src;   // store byte offset of the chunk's first 16-byte block
+    uint64_t w0;    // the entry's first output word
+    uint64_t sw0;   // the chunk's first word in the store's word space
+    uint32_t mis, len, n, nblk, flags;
+    bool big;       // decodable, but too large for the tables alone
+};
+
+__device__ __forceinline__ SelLane sel_load(const uint8_t* __restrict__ in,
+                                            const SelRec* __restrict__ rec,
+                                            const uint64_t* __restrict__ out_off, uint64_t ia,
+                                            uint32_t nc, uint32_t lane, uint64_t cap) {
+    SelLane e{};
+    if (lane < nc) {
+        const uint4* rp = reinterpret_cast<const uint4*>(rec + ia + lane);
+        const uint4 ra = rp[0], rb = rp[1];
+        const uint64_t w0 = out_off[ia + lane], w1 = out_off[ia + lane + 1];
+        const uint64_t pb = ((uint64_t)ra.y << 32) | ra.x;
+        e.sw0 = ((uint64_t)ra.w << 32) | ra.z;
+        e.flags = rb.y;
+        if (!(e.flags & kSelInvalid) && w1 > cap) e.flags |= kSelShort;
+        const uint64_t n64 = (e.flags & (kSelInvalid | kSelShort)) ? 0ull : w1 - w0;
+        e.w0 = w0;
+        e.len = rb.x;
+        e.mis = (uint32_t)(reinterpret_cast<uintptr_t>(in + pb) & 15u);
+        e.src = pb - e.mis;
+        const bool need = n64 > 0 && e.len > 0;
+        // (len < 2^31: no wrap)
+        const uint32_t nblk = need ? (e.mis + e.len + 15u) / 16u : 0u;
+        e.big = n64 > kTileWords || nblk > kSelBlocks || ((e.flags & kSelHuge) && n64 > 0);
+        e.n = e.big ? 0u : (uint32_t)n64;
+        e.nblk = e.big ? 0u : nblk;
+    }
+    return e;
+}
+
+// Position among the entries [lo, lo + k) (lane = entry, x = its exclusive
+// count of blocks or segments, non-decreasing) of the last one with x <= b:
+// the entry that holds item b (entries without items share their
+// successor's count and are passed over).
+__device__ __forceinline__ uint32_t sel_find(uint32_t x, uint32_t lo, uint32_t k, uint32_t b) {
+    uint32_t c = 0;
+    for (uint32_t q = 1; q < k; q++)
+        c += (uint32_t)__builtin_amdgcn_readlane((int)x, (int)(lo + q)) <= b ? 1u : 0u;
+    return c;
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, uint32_t l) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)l, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), (int)l, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// Start state of segment j of a chunk (bytes [cs, pe), words [wa, wz) of the
+// tile) whose first word is sb: the tag position q and the word w.  ent is
+// the index entry of sb's store word: the record covering it, and if that
+// record is a run with its head before sb, the segment starts after it.
+// false: the entry is unusable.
+__device__ __forceinline__ bool sel_seg_start(const uint8_t* B, uint32_t cs, uint32_t pe,
+                                              uint32_t wa, uint32_t wz, uint32_t sb, uint32_t j,
+                                              uint32_t ent, uint32_t& q, uint32_t& w) {
+    q = cs;
+    w = wa;
+    if (j == 0) return true;
+    const uint32_t off = ent & 0xFFFFFFu, d = ent >> 24;
+    if (ent == kSyncNone || off >= pe - cs || d > sb - wa) return false;
+    q = cs + off;
+    w = sb;
+    if (d) {  // skip the run that covers sb
+        uint32_t tag, b1, b9;
+        rec_bytes(B, q + 1u, tag, b1, b9);
+        const bool isz = tag == 0, isf = tag == 0xFF;
+        const uint32_t cnt = isz ? b1 : b9;
+        const uint32_t qe = isz ? q + 2u : q + 10u + 8u * cnt;
+        const uint32_t wn = sb - d + 1u + cnt;
+        if (!(isz || isf) || wn <= sb || wn > wz || qe > pe) return false;
+        q = qe;
+        w = wn;
+    }
+    return true;
+}
+
+// Walks segment j of chunk c from the record the index names until its word
+// reaches the segment end, with every record checked against the chunk's
+// bytes and words; its end state must be the next segment's start (or the
+// chunk's end).  Any failure marks the chunk for the exact walk, so the index
+// changes the speed only.  Returns true if it marked the chunk.
+__device__ __forceinline__ bool sel_walk_seg(SelSmem& S, uint32_t c, uint32_t j, uint32_t ent,
+                                             uint32_t entn) {
+    const uint8_t* B = S.bytes;
+    const uint32_t cs = S.cp[c], pe = S.ce[c], wa = S.cw[c], wz = S.cw[c + 1];
+    const uint32_t r = S.rr[c];
+    const uint32_t ns = (r + (wz - wa) + kSyncWords - 1) / kSyncWords;
+    const uint32_t sb = j == 0 ? wa : wa + kSyncWords * j - r;
+    const uint32_t eb = j + 1 == ns ? wz : wa + kSyncWords * (j + 1) - r;
+    uint32_t q, w;
+    bool ok = sel_seg_start(B, cs, pe, wa, wz, sb, j, ent, q, w);
+    while (ok && w < eb) {
+        uint32_t tag, b1, b9;
+        rec_bytes(B, q + 1u, tag, b1, b9);  // (q <= pe: inside the staged bytes and their slack)
+        const bool isz = tag == 0, isf = tag == 0xFF;
+        const uint32_t cnt = isz ? b1 : (isf ? b9 : 0u);
+        const uint32_t qe = q + 1u + __builtin_popcount(tag) + ((isz || isf) ? 1u : 0u) +
+                            (isf ? 8u * cnt : 0u);
+        const uint32_t wn = w + 1u + cnt;
+        // (the record, with its run count and literal bytes, lies in the chunk)
+        ok = qe <= pe && wn <= wz;
+        if (ok) {
+            S.dpos[w] = (uint16_t)q;
+            if (isf && cnt) lit_entries(S, w, q, cnt);
+            q = qe;
+            w = wn;
+        }
+    }
+    if (ok) {
+        if (j + 1 == ns) {
+            ok = w == wz && q == pe;
+        } else {
+            uint32_t q2, w2;
+            ok = sel_seg_start(B, cs, pe, wa, wz, eb, j + 1, entn, q2, w2) && q2 == q && w2 == w;
+        }
+    }
+    if (!ok) S.badc[c] = 1;
+    return !ok;
+}
+
+// One staged sub-tile: entries [lo, lo + k) of the tile (lanes lo.. of `e`),
+// none of them big, whose words and blocks fit the tables.  All threads of
+// the workgroup call it.  i0 = the index of entry lo.
+template <bool SYNC>
+__device__ __forceinline__ void select_subtile(SelSmem& S, const uint8_t* __restrict__ in,
+                                               const SelLane& e, uint32_t lo, uint32_t k,
+                                               uint64_t i0, uint64_t* __restrict__ out,
+                                               int32_t* __restrict__ status,
+                                               uint64_t* __restrict__ consumed, uint64_t cap,
+                                               const uint32_t* __restrict__ sync, uint32_t tid,
+                                               uint32_t lane, uint32_t wave) {
+    const bool mine = lane >= lo && lane < lo + k;
+    const uint32_t xn = mine ? e.n : 0u, xb = mine ? e.nblk : 0u;
+    // (entries are lanes 0..15: one DPP row)
+    const uint32_t iw = row_sum_scan(xn), ib = row_sum_scan(xb);
+    const uint32_t Wt = (uint32_t)__builtin_amdgcn_readlane((int)iw, (int)(lo + k - 1u));
+    const uint32_t Bt = (uint32_t)__builtin_amdgcn_readlane((int)ib, (int)(lo + k - 1u));
+    const uint64_t W0 = readlane64(e.w0, lo);
+    const uint32_t eb = ib - xb;  // the entry's first staged block
+    // gather: every load issued before the tables are written (the entry of a
+    // block or segment comes from the lanes' registers, no LDS round trip)
+    constexpr uint32_t kLoads = (kSelBlocks + kThreads - 1) / kThreads;
+    uint4 r[kLoads];
+#pragma unroll
+    for (uint32_t u = 0; u < kLoads; u++) {
+        const uint32_t b = tid + u * kThreads;
+        const uint32_t c = lo + sel_find(eb, lo, k, b);
+        const uint64_t src = shfl64(e.src, c);
+        const uint32_t b0 = (uint32_t)__shfl((int)eb, (int)c, 64);
+        r[u] = make_uint4(0, 0, 0, 0);
+        if (b < Bt) r[u] = *reinterpret_cast<const uint4*>(in + src + 16ull * (b - b0));
+    }
+    // sync segments: a chunk whose first store word is 8 m + r has
+    // ceil((r + n) / 8) of them, segment j >= 1 starting at store word
+    // 8 (m + j), which is index entry m + j
+    constexpr uint32_t kSegs = SYNC ? (kSelSegs + kThreads - 1) / kThreads : 1;
+    uint32_t sc[kSegs], sj[kSegs], se[kSegs], sn[kSegs];
+    uint32_t Ns = 0;
+    if constexpr (SYNC) {
+        const uint32_t rr = (uint32_t)e.sw0 & (kSyncWords - 1);
+        const uint32_t xs = xn ? (rr + xn + kSyncWords - 1) / kSyncWords : 0u;
+        const uint32_t is = row_sum_scan(xs);
+        const uint32_t es = is - xs;
+        Ns = (uint32_t)__builtin_amdgcn_readlane((int)is, (int)(lo + k - 1u));
+#pragma unroll
+        for (uint32_t u = 0; u < kSegs; u++) {
+            const uint32_t b = tid + u * kThreads;
+            const uint32_t c = lo + sel_find(es, lo, k, b);
+            const uint32_t j = b - (uint32_t)__shfl((int)es, (int)c, 64);
+            const uint32_t nsc = (uint32_t)__shfl((int)xs, (int)c, 64);
+            const uint64_t kb = shfl64(e.sw0 / kSyncWords, c) + j;
+            sc[u] = c - lo;
+            sj[u] = j;
+            se[u] = sn[u] = kSyncNone;
+            if (b < Ns && j >= 1) se[u] = sync[kb];
+            if (b < Ns && j + 1 < nsc) sn[u] = sync[kb + 1];
+        }
+    }
+    if (wave == 0 && mine) {
+        const uint32_t c = lane - lo;
+        const uint32_t p = 16u * eb + e.mis;
+        S.cw[c] = iw - xn;
+        S.cp[c] = p;
+        S.ce[c] = p + (xb ? e.len : 0u);
+        S.fl[c] = (uint8_t)e.flags;
+        S.rr[c] = (uint8_t)((uint32_t)e.sw0 & (kSyncWords - 1));
+        if (c + 1u == k) S.cw[k] = iw;
+    }
+    {
+        uint4* dd = reinterpret_cast<uint4*>(S.dpos);
+        const uint4 none = make_uint4(~0u, ~0u, ~0u, ~0u);
+        for (uint32_t q = tid; q < (Wt + 7) / 8; q += kThreads) dd[q] = none;
+        S.sel[tid] = kExpandTable.s[tid];
+        if (tid < kStageChunks) S.badc[tid] = 0;
+        uint4* dst = reinterpret_cast<uint4*>(S.bytes);
+#pragma unroll
+        for (uint32_t u = 0; u < kLoads; u++)
+            if (tid + u * kThreads < Bt) dst[tid + u * kThreads] = r[u];
+    }
+    __syncthreads();
+    if constexpr (SYNC) {
+        bool marked = false;
+#pragma unroll
+        for (uint32_t u = 0; u < kSegs; u++)
+            if (tid + u * kThreads < Ns) marked |= sel_walk_seg(S, sc[u], sj[u], se[u], sn[u]);
+        const bool anybad = __syncthreads_or(marked);
+        if (tid < k) {
+            const uint64_t cc = i0 + tid;
+            const uint32_t wa = S.cw[tid], wz = S.cw[tid + 1];
+            if (anybad && S.badc[tid]) {  // exact serial walk of the chunk
+                for (uint32_t i = wa; i < wz; i++) S.dpos[i] = kNone;
+                int32_t st;
+                uint32_t used;
+                walk_chunk(S, S.cp[tid], S.ce[tid], wa, wz - wa, st, used);
+                status[cc] = st;
+                if (consumed) consumed[cc] = used;
+            } else {
+                status[cc] = ST_OK;
+                if (consumed) consumed[cc] = wz > wa ? S.ce[tid] - S.cp[tid] : 0u;
+            }
+        }
+    } else {
+        spec_seg_tile(S, i0, k, status, consumed, tid, lane);
+    }
+    if (tid < k && (S.fl[tid] & (kSelInvalid | kSelShort))) {  // (zero words: walked as empty)
+        status[i0 + tid] = (S.fl[tid] & kSelInvalid) ? (int32_t)CAPNP_E_INVALID_ARGUMENT
+                                                     : (int32_t)CAPNP_E_BUFFER_NOT_LARGE_ENOUGH;
+        if (consumed) consumed[i0 + tid] = 0;
+    }
+    __syncthreads();
+    {
+        const uint32_t ng = (Wt + CAPNP_WAVE - 1) / CAPNP_WAVE;
+        for (uint32_t g0 = wave; g0 < ng; g0 += kGroups * kWaves) {
+            uint32_t d[kGroups];
+#pragma unroll
+            for (int u = 0; u < (int)kGroups; u++) {
+                const uint32_t i = (g0 + u * kWaves) * CAPNP_WAVE + lane;
+                d[u] = i < Wt ? S.dpos[i] : kNone;
+            }
+#pragma unroll
+            for (int u = 0; u < (int)kGroups; u++) {
+                const uint32_t i = (g0 + u * kWaves) * CAPNP_WAVE + lane;
+                const uint64_t word = expand_desc<FIT_SEL_ALU>(S.bytes, S.sel, d[u]);
+                if (i < Wt && W0 + i < cap) out[W0 + i] = word;
+            }
+        }
+    }
+}
+
+template <bool SYNC>
+__global__ void __launch_bounds__(kThreads, 8)
+select_fit_kernel(const uint8_t* __restrict__ in, const SelRec* __restrict__ rec, uint64_t nsel,
+                  uint64_t* __restrict__ out, uint64_t cap, const uint64_t* __restrict__ out_off,
+                  int32_t* __restrict__ status, uint64_t* __restrict__ consumed,
+                  const uint32_t* __restrict__ sync, uint32_t* __restrict__ novf,
+                  uint32_t* __restrict__ ovf) {
+    __shared__ SelSmem S;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint64_t ia = (uint64_t)blockIdx.x * kSelTile;
+    const uint32_t nc = (uint32_t)(nsel - ia < kSelTile ? nsel - ia : kSelTile);
+    const SelLane e = sel_load(in, rec, out_off, ia, nc, lane, cap);
+    const uint32_t tw = row_sum_scan(e.n), tb = row_sum_scan(e.nblk);
+    const uint32_t Wt = (uint32_t)__builtin_amdgcn_readlane((int)tw, (int)(kSelTile - 1));
+    const uint32_t Bt = (uint32_t)__builtin_amdgcn_readlane((int)tb, (int)(kSelTile - 1));
+    if ((ballot64(e.big) & 0xFFFFull) || Wt > kTileWords || Bt > kSelBlocks) {
+        if (tid == 0) ovf[atomicAdd(novf, 1u)] = blockIdx.x;
+        return;
+    }
+    select_subtile<SYNC>(S, in, e, 0, nc, ia, out, status, consumed, cap, sync, tid, lane, wave);
+}
+
+// (three waves per SIMD: at four the long-unit decode spilled 48 bytes a lane)
+__global__ void __launch_bounds__(kThreads, 3)
+select_ovf_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                  const uint64_t* __restrict__ ids, const SelRec* __restrict__ rec,
+                  uint64_t nsel, uint64_t* __restrict__ out, uint64_t cap,
+                  const uint64_t* __restrict__ out_off, int32_t* __restrict__ status,
+                  uint64_t* __restrict__ consumed, const uint32_t* __restrict__ novf,
+                  const uint32_t* __restrict__ ovf) {
+    __shared__ SelUSmem sm;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t n = uniform(*novf);
+    for (uint32_t t = blockIdx.x; t < n; t += gridDim.x) {
+        const uint64_t ia = (uint64_t)uniform(ovf[t]) * kSelTile;
+        const uint32_t nc = (uint32_t)(nsel - ia < kSelTile ? nsel - ia : kSelTile);
+        const SelLane e = sel_load(in, rec, out_off, ia, nc, lane, cap);
+        const uint32_t bigm = (uint32_t)(ballot64(e.big) & 0xFFFFull);
+        for (uint32_t lo = 0; lo < nc;) {
+            __syncthreads();  // the previous sub-tile is done with LDS
+            if ((bigm >> lo) & 1u) {
+                // the long-unit decode reads in_off[c], in_off[c + 1] and
+                // writes entry c: c = i, the byte offsets shifted to id
+                const uint64_t i = ia + lo;
+                const uint64_t id = uniform64(ids[i]);
+                const uint64_t* io = reinterpret_cast<const uint64_t*>(
+                    reinterpret_cast<uintptr_t>(in_off) + 8ull * id - 8ull * i);
+                unpack_long(sm.u, in, io, i, out, out_off, status, consumed, tid, lane, wave);
+                lo += 1;
+                continue;
+            }
+            // the longest prefix of [lo, next big entry) that fits
+            const uint32_t rest = bigm >> lo;
+            const uint32_t hi = rest ? lo + (uint32_t)__builtin_ctz(rest) : nc;
+            const bool in_r = lane >= lo && lane < hi;
+            const uint32_t iw = row_sum_scan(in_r ? e.n : 0u);
+            const uint32_t ib = row_sum_scan(in_r ? e.nblk : 0u);
+            const uint32_t k = (uint32_t)__builtin_popcountll(
+                ballot64(in_r && iw <= kTileWords && ib <= kSelBlocks) & 0xFFFFull);
+            select_subtile<false>(sm.st, in, e, lo, k, ia + lo, out, status, consumed, cap,
+                                  nullptr, tid, lane, wave);
+            lo += k;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 // Output words per unpack tile the staged path is sized for; the host picks
@@ -3227,6 +3651,68 @@ extern "C" hipError_t capnp_launch_unpack(const uint8_t* d_in, const uint64_t* d
                            dim3(kThreads), 0, stream, d_in, d_in_off, nchunks, tc, d_out,
                            d_out_off, d_status, d_consumed, d_sync, blocks);
     }
+    return hipGetLastError();
+}
+
+// Selective unpack: workspace and launch.  The workspace holds the overflow
+// tile count (16 bytes), the entry records, the entries' word counts, the
+// overflow tile list and the scan's temporary storage.  The geometry of all
+// three kernels depends on nsel alone.
+extern "C" hipError_t capnp_scan_counts(const uint64_t*, uint64_t, uint64_t*, void*, size_t,
+                                        hipStream_t);
+extern "C" size_t capnp_scan_counts_tmp_bytes(uint64_t n);
+
+namespace {
+struct SelWs {
+    size_t rec, len, list, tmp, tmp_bytes, end;
+};
+SelWs sel_ws(uint64_t nsel) {
+    const auto r16 = [](size_t x) { return (x + 15) & ~size_t(15); };
+    const uint64_t ntiles = (nsel + kSelTile - 1) / kSelTile;
+    SelWs w;
+    w.rec = 16;
+    w.len = w.rec + sizeof(SelRec) * nsel;
+    w.list = w.len + r16(8 * nsel);
+    w.tmp = w.list + r16(4 * ntiles);
+    w.tmp_bytes = capnp_scan_counts_tmp_bytes(nsel);
+    w.end = w.tmp + r16(w.tmp_bytes);
+    return w;
+}
+}  // namespace
+
+extern "C" size_t capnp_unpack_select_ws_bytes(uint64_t nsel) { return sel_ws(nsel).end; }
+
+extern "C" hipError_t capnp_launch_unpack_select(
+    const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_word_off, uint64_t nstore,
+    const uint64_t* d_ids, uint64_t nsel, const uint32_t* d_sync, uint64_t* d_out,
+    uint64_t words_cap, uint64_t* d_out_off, int32_t* d_status, uint64_t* d_consumed,
+    uint8_t* d_ws, size_t ws_bytes, hipStream_t stream) {
+    if (nsel == 0) return hipMemsetAsync(d_out_off, 0, 8, stream);
+    const SelWs w = sel_ws(nsel);
+    if (ws_bytes < w.end) return hipErrorInvalidValue;
+    uint32_t* novf = reinterpret_cast<uint32_t*>(d_ws);
+    SelRec* rec = reinterpret_cast<SelRec*>(d_ws + w.rec);
+    uint64_t* len = reinterpret_cast<uint64_t*>(d_ws + w.len);
+    uint32_t* list = reinterpret_cast<uint32_t*>(d_ws + w.list);
+    const uint64_t ntiles = (nsel + kSelTile - 1) / kSelTile;
+    hipLaunchKernelGGL(select_prep_kernel, dim3((uint32_t)((nsel + 255) / 256)), dim3(256), 0,
+                       stream, d_in_off, d_word_off, nstore, d_ids, nsel, rec, len, novf);
+    hipError_t e = capnp_scan_counts(len, nsel, d_out_off, d_ws + w.tmp, w.tmp_bytes, stream);
+    if (e != hipSuccess) return e;
+    // (the tiles that fit walk through the index when there is one; the
+    // overflow tiles never do)
+    if (d_sync)
+        hipLaunchKernelGGL(select_fit_kernel<true>, dim3((uint32_t)ntiles), dim3(kThreads), 0,
+                           stream, d_in, rec, nsel, d_out, words_cap, d_out_off, d_status,
+                           d_consumed, d_sync, novf, list);
+    else
+        hipLaunchKernelGGL(select_fit_kernel<false>, dim3((uint32_t)ntiles), dim3(kThreads), 0,
+                           stream, d_in, rec, nsel, d_out, words_cap, d_out_off, d_status,
+                           d_consumed, d_sync, novf, list);
+    hipLaunchKernelGGL(select_ovf_kernel,
+                       dim3((uint32_t)(ntiles < kSelOvfGrid ? ntiles : kSelOvfGrid)),
+                       dim3(kThreads), 0, stream, d_in, d_in_off, d_ids, rec, nsel, d_out,
+                       words_cap, d_out_off, d_status, d_consumed, novf, list);
     return hipGetLastError();
 }
 

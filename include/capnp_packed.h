@@ -242,6 +242,56 @@ capnp_status capnp_gpu_unpack_batch_sync_tuned(capnp_ctx* ctx, const uint8_t* d_
                                                uint64_t* d_consumed, uint32_t chunks_per_tile,
                                                void* stream);
 
+/* ---- selective unpack: chosen chunks of a packed store, by id ---- */
+/* Decode the chunks d_ids[0..nsel) of a packed store, in that order, into
+   d_words back to back.  The store is what capnp_gpu_pack_batch[_sync] wrote:
+   chunk c is packed bytes [d_in_byte_off[c], d_in_byte_off[c+1]) of d_packed
+   and decodes to d_chunk_word_off[c+1] - d_chunk_word_off[c] words (both
+   arrays nstore+1 entries).
+   Entry i is the batch decode of chunk id = d_ids[i]: d_status[i],
+   d_consumed[i] (may be NULL) and the words are exactly what
+   capnp_gpu_unpack_batch gives chunk id of the store (PackedRead::read under
+   read_exact, serialize_packed.rs:80-228, io.rs:16-31); the words land at
+   d_words[d_out_word_off[i] .. d_out_word_off[i+1]).  Any id list is legal:
+   ids may repeat, come in any order and cover none or all of the store.
+   d_out_word_off (nsel+1 entries) is WRITTEN by the call, on the device: the
+   exclusive sum of the selected chunks' word counts, d_out_word_off[nsel] the
+   total words needed.  Words of an entry with a non-OK status are unspecified
+   but stay inside that entry's own range; nothing outside
+   [0, min(total, words_cap)) is written.
+   words_cap short (the convention of capnp_gpu_pack_batch's out_cap, per
+   entry): an entry whose range ends past words_cap gets
+   CAPNP_E_BUFFER_NOT_LARGE_ENOUGH and consumed 0, none of its words at or
+   past words_cap are written, the offsets still report the size that was
+   needed, and the call returns CAPNP_OK.
+   Validation is per entry only: id >= nstore, d_in_byte_off[id] >
+   d_in_byte_off[id+1] or d_chunk_word_off[id] > d_chunk_word_off[id+1] give
+   that entry CAPNP_E_INVALID_ARGUMENT, zero words and consumed 0, and leave
+   the others alone.  The store's offset arrays are not scanned: the cost of
+   a call scales with the selection, not with the store.
+   d_sync (may be NULL) is the index capnp_gpu_pack_batch_sync wrote for this
+   store with these d_chunk_word_off.  It can only accelerate: a missing,
+   all-0xFFFFFFFF, corrupt or foreign index gives identical results: each
+   chunk is cut where its store words cross a multiple of CAPNP_SYNC_WORDS,
+   the segments' walks must meet and end at the chunk's packed end, and a
+   chunk that fails any check takes the exact serial walk.  (Chunks too large
+   for the staged tile decode without it.)
+   Stream-ordered, no host wait once the context's workspace covers nsel (it
+   grows on first use; capnp_ctx_reserve(ctx, n) covers selections of up to n
+   entries); the launch geometry depends on nsel alone.  nsel == 0 writes
+   d_out_word_off[0] = 0 and launches nothing else; nsel >= 2^31 - 1 is
+   CAPNP_E_INVALID_ARGUMENT.  Reads of d_packed stay inside the 16-byte
+   aligned blocks that overlap a selected chunk's own bytes, as the batch
+   decode's. */
+capnp_status capnp_gpu_unpack_batch_select(
+    capnp_ctx* ctx, const uint8_t* d_packed, const uint64_t* d_in_byte_off,
+    const uint64_t* d_chunk_word_off, size_t nstore,
+    const uint64_t* d_ids, size_t nsel,
+    const uint32_t* d_sync,            /* the store's record sync index, or NULL */
+    uint64_t* d_words, size_t words_cap,
+    uint64_t* d_out_word_off,          /* nsel+1, WRITTEN by the call */
+    int32_t* d_status, uint64_t* d_consumed /* may be NULL */, void* stream);
+
 
 /* ---- index-free decode of long read units ---------- */
 /* The same transform, statuses and consumed counts as capnp_gpu_unpack_batch
